@@ -1,7 +1,14 @@
 """Benchmark: RS(10+2) encode+decode GiB/s, device-resident, 1 MiB objects.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload encdec|enc|dec4]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last step's
+outputs if --dump-outputs is given, and prints the headline fields (metric,
+value, unit, ms_per_step, dtype, config).  Everything else described below
+(strong_scaling, work_check, roofline with its PMC passes, warm_repeat,
+cpu_baseline) runs after the timed steps only with --full.
 
 A step = one pass of the hot path over one batch: encode the batch (parity
 rows <- M x data rows, Client.encode / ecRedis.go:390) then decode it
@@ -14,7 +21,7 @@ with --collectives) the same line carries a `strong_scaling` block: the
 workload's one batch split over the ranks (shard_objects), timed after the
 weak region with the same barriers.
 
-Prints ONE JSON line (rank 0) with roofline (HIP-event kernel timing;
+Prints ONE JSON line (rank 0); with --full it carries roofline (HIP-event kernel timing;
 `traffic` measured in this run by two rocprofv3 --pmc child passes at N = 1,
 else the committed summary, `traffic_source` says which) and cpu_baseline
 (the oracle's AVX-512/AVX2 port of the Go path, timed on this host by rank 0
@@ -382,6 +389,33 @@ def shard_objects(nobj_total: int, rank: int, world: int):
     return start, base + (1 if rank < rem else 0)
 
 
+DUMP_ELEMS = 12 << 20  # --dump-outputs: sampled bytes per rank, 48 MiB as float32
+
+
+def dump_index(nobj, nrows, S, seed=0xD0F1):
+    """The fixed, seeded sample --dump-outputs takes of a batch's written rows:
+    (objects, byte columns), both sorted, the first and last of each always
+    in, at most DUMP_ELEMS bytes over `nrows` rows per object.  Every object
+    is sampled while 256 columns of each fit; past that, fewer objects."""
+    rng = np.random.default_rng(seed)
+
+    def pick(total, cnt):
+        if cnt >= total:
+            return np.arange(total, dtype=np.int64)
+        mid = rng.choice(total - 2, max(0, cnt - 2), replace=False) + 1 if total > 2 else []
+        return np.unique(np.concatenate([[0, total - 1], mid])).astype(np.int64)
+
+    ncols = min(S, max(256, DUMP_ELEMS // (nobj * nrows)))
+    return pick(nobj, max(1, DUMP_ELEMS // (nrows * ncols))), pick(S, ncols)
+
+
+def dump_save(dirname, name, arr, rank=0):
+    """DIR/<name>.npy (rank 0; other ranks DIR/<name>.rank<r>.npy), float32."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + (f".rank{rank}" if rank else "") + ".npy"),
+            np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def timed_run(step, steps, warmup, sync, dctx: DistCtx):
     """W untimed warmup steps; barrier + sync; K timed steps; sync + barrier +
     sync; returns the MAX over ranks of the elapsed seconds."""
@@ -450,7 +484,7 @@ def _pmc_child(args, counters, timeout=90, warmup=3):
     child_env["BENCH_PMC_CHILD"] = "1"
     with tempfile.TemporaryDirectory(prefix="bench_pmc_", dir=os.environ.get("TMPDIR", "/tmp")) as out:
         cmd = [exe, "--pmc", *counters, "-d", out, "-o", "run", "--output-format", "csv", "--",
-               sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--no-cpu",
+               sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--full", "--no-cpu",
                "--no-pmc", "--steps", "3", "--warmup", str(warmup), "--copies", str(args.copies)]
         if args.batch:
             cmd += ["--batch", str(args.batch)]
@@ -577,7 +611,8 @@ def run_trace(args):
     enc = ia.New(k, p, devices=list(range(ndev))) if ndev > 1 else ia.New(k, p)
     host = ia.host_alloc(int(offs[-1]))
     # random object bytes: one 256 MiB device random block, copied around
-    rnd = torch.randint(0, 256, (256 << 20,), dtype=torch.uint8, device="cuda").cpu().numpy()
+    rgen = torch.Generator(device="cuda").manual_seed(20200225)
+    rnd = torch.randint(0, 256, (256 << 20,), dtype=torch.uint8, device="cuda", generator=rgen).cpu().numpy()
     objs = []
     for o in range(nobj):
         base = host[offs[o]:offs[o + 1]]
@@ -629,6 +664,17 @@ def run_trace(args):
     for _ in range(args.steps):
         step()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the rows the last step wrote (parity, then the rebuilt data rows),
+        # object after object from the first, up to DUMP_ELEMS bytes
+        parts, left = [], DUMP_ELEMS
+        for o in range(nobj):
+            for i in list(range(k, n)) + list(lost):
+                parts.append(objs[o][i][:left])
+                left -= len(parts[-1])
+            if left <= 0:
+                break
+        dump_save(args.dump_outputs, "rows_written", np.concatenate(parts))
     for j, o in enumerate(range(0, nobj, 37)):
         for g, i in zip(golden[j], lost):
             assert np.array_equal(objs[o][i], g), "decode did not restore the data rows"
@@ -871,7 +917,20 @@ def main():
     ap.add_argument("--no-pmc", action="store_true",
                     help="take roofline.traffic from the committed PMC summary instead of two rocprofv3 "
                          "--pmc child passes of this workload (the default at N = 1 when rocprofv3 is present)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the line can carry: the strong-"
+                         "scaling block, the work check, per-kernel timing and the roofline with its PMC "
+                         "child passes, --warm, and the CPU baseline.  Without it a run sets up, warms up, "
+                         "times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy "
+                         "(float32): a fixed, seeded sample of the rows it wrote (rows_written) and the "
+                         "decode's per-object flags (decode_flags)")
     args = ap.parse_args()
+    if args.warm and not args.full:
+        ap.error("--warm is part of the --full report: add --full")
+    if args.dump_outputs and args.workload == "latency":
+        ap.error("--dump-outputs: the latency workload keeps no output batch")
     if args.warmup is None:
         # ~0.1-0.2 s of untimed steps: the HBM-bound workloads time the same
         # with 3 or 1000 (the headline: 4,530-4,555 GiB/s), but the VALU-
@@ -1122,6 +1181,70 @@ def main():
     if int(bad.sum()) != 0:
         raise SystemExit("decode reported a verify mismatch on synthetic data")
 
+    if args.dump_outputs:
+        # what the last timed step left in its batch, before anything else
+        # touches it: the rows its ops wrote (every row where the erasures
+        # differ per object), sampled by dump_index, and the decode's flags
+        last = bufs[(turn[0] - 1) % copies]
+        if w.get("mixed"):
+            rows = list(range(n))
+        else:
+            rows = sorted({i for op in w["ops"] for i in torch.nonzero(written[op][0]).flatten().tolist()})
+        oi, ci = dump_index(nobj, len(rows), S)
+        v = last[:, :nobj * stride].view(n, nobj, stride).permute(1, 0, 2) if w.get("shard_major") else last
+        oi_d, ci_d = torch.from_numpy(oi).to(dev), torch.from_numpy(ci).to(dev)
+        ri_d = torch.tensor(rows, dtype=torch.int64, device=dev)
+        dump_save(args.dump_outputs, "rows_written",
+                  v[oi_d[:, None, None], ri_d[None, :, None], ci_d[None, None, :]].cpu().numpy(), rank)
+        if "decode" in w["ops"] and not w.get("data_only"):
+            dump_save(args.dump_outputs, "decode_flags", bad.cpu().numpy(), rank)
+
+    def headline(value, ms_per_step):
+        return {
+            "metric": METRICS[args.workload],
+            "value": round(value, 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "strong" if args.strong else "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": f"synthetic: uniform random bytes (torch.randint on device, seeded per rank), "
+                    f"{copies} distinct batches coded in rotation",
+            "config": {
+                "workload": w["desc"],
+                "k": k, "p": p,
+                "object_bytes": w["nbytes"],
+                "shard_len": S,
+                "pitch": pitch,
+                "obj_stride": stride,
+                "layout": "shard-major" if w.get("shard_major") else "object-major",
+                "batch_per_gpu": nobj,
+                "batch_copies": copies,
+                "decode_erasures": list(w["lost"]),
+                "parallelism": (f"object-per-rank x{world} "
+                                + ("(one process, no collective)" if not dist_on else
+                                   f"({'RCCL' if backend == 'nccl' else backend} all_reduce barrier only"
+                                   + (", ranks sharing one GPU)" if os.environ.get("BENCH_SHARE_GPU") == "1"
+                                      else ")"))),
+            },
+        }
+
+    if not args.full:
+        # the plain run ends here: the headline fields of the timed steps
+        if rank == 0:
+            out = headline(objs_all * w["nbytes"] * len(w["ops"]) * args.steps / elapsed / GiB,
+                           elapsed / args.steps * 1e3)
+            if dist_on:
+                out["collectives_issued"] = dctx.calls
+            print(json.dumps(out), flush=True)
+        if dist_on:
+            dist.destroy_process_group()
+        return
+
     # Strong scaling beside the weak line ("strong
     # scaling of 1024 total"): the workload's ONE batch split over the ranks
     # by shard_objects, each rank coding its share (a prefix of its own
@@ -1298,36 +1421,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": METRICS[args.workload],
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": f"synthetic: uniform random bytes (torch.randint on device, seeded per rank), "
-                    f"{copies} distinct batches coded in rotation",
-            "config": {
-                "workload": w["desc"],
-                "k": k, "p": p,
-                "object_bytes": w["nbytes"],
-                "shard_len": S,
-                "pitch": pitch,
-                "obj_stride": stride,
-                "layout": "shard-major" if w.get("shard_major") else "object-major",
-                "batch_per_gpu": nobj,
-                "batch_copies": copies,
-                "decode_erasures": list(w["lost"]),
-                "parallelism": (f"object-per-rank x{world} "
-                                + ("(one process, no collective)" if not dist_on else
-                                   f"({'RCCL' if backend == 'nccl' else backend} all_reduce barrier only"
-                                   + (", ranks sharing one GPU)" if os.environ.get("BENCH_SHARE_GPU") == "1"
-                                      else ")"))),
-            },
+            **headline(value, ms_per_step),
             "roofline": roofline,
             **({"decode_check": work_check["decode"]["result"]} if "decode" in work_check else {}),
             "work_check": work_check,

@@ -111,3 +111,19 @@ def test_pmc_sq_summary_from_a_counter_csv(tmp_path):
     assert sm["valu_active_share_of_simd_cycles"] == round(4 * 1_024_000 / (1024 * 4000), 4)  # 1.0
     assert sm["wait_any_over_wave_cycles"] == 0.5
     assert sm["clock_GHz_pass_duration"] == 2.0  # 4000 cycles / 2000 ns
+
+
+def test_dump_index_is_a_fixed_bounded_sample():
+    """bench.py --dump-outputs samples the same objects and columns in every
+    run, the first and last of each included, within its size budget."""
+    for nobj, nrows, S in ((1024, 4, 104858), (1 << 20, 4, 103), (16, 4, 104858), (262144, 12, 410), (3, 2, 1)):
+        oi, ci = bench.dump_index(nobj, nrows, S)
+        oi2, ci2 = bench.dump_index(nobj, nrows, S)
+        assert np.array_equal(oi, oi2) and np.array_equal(ci, ci2)
+        assert len(oi) * nrows * len(ci) <= bench.DUMP_ELEMS and bench.DUMP_ELEMS * 4 <= 64 * 10**6
+        for idx, total in ((oi, nobj), (ci, S)):
+            assert idx[0] == 0 and idx[-1] == total - 1 and np.all(np.diff(idx) > 0)
+    oi, ci = bench.dump_index(1024, 4, 104858)
+    assert len(oi) == 1024 and len(ci) == 3072   # the headline: every object, 3 % of its columns
+    oi, ci = bench.dump_index(16, 4, 104858)
+    assert len(oi) == 16 and len(ci) == 104858   # a small batch whole

@@ -24,14 +24,14 @@ for s in $STEPS; do
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     soak)   RSGPU_SOAK_SECONDS=${SOAK_SECONDS:-240} RSGPU_SOAK_SEED=${SOAK_SEED:-20261016} run soak $(( ${SOAK_SECONDS:-240} + 240 )) python -u -m pytest tests/test_gpu_soak.py -m gpu -x -s --timeout $(( ${SOAK_SECONDS:-240} + 200 )) --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py ;;
+    bench)  run bench 600 python bench.py --full ;;
     bench_all)
-            run bench_enc 300 python bench.py --workload enc --no-cpu
-            run bench_dec4 300 python bench.py --workload dec4 --no-cpu
-            run bench_mixed 300 python bench.py --workload encdec_mixed --no-cpu ;;
+            run bench_enc 300 python bench.py --workload enc --full --no-cpu
+            run bench_dec4 300 python bench.py --workload dec4 --full --no-cpu
+            run bench_mixed 300 python bench.py --workload encdec_mixed --full --no-cpu ;;
     allwl)  # every device-resident workload once (value, frac, per-op kernel ms, decode check)
             for wl in ${ALL_WLS:-enc dec4 encdec_mixed encdec_upstream small small_mixed small1k small1k_sm small1k_sm_mixed_a128 wide}; do
-              run wl_$wl 300 python bench.py --workload $wl --no-cpu --no-pmc
+              run wl_$wl 300 python bench.py --workload $wl --full --no-cpu --no-pmc
             done
             run wl_trace 600 python bench.py --workload trace --steps 3 --warmup 1 --no-cpu
             python - > gpurun_out/all_workloads.txt <<'PY'
@@ -46,13 +46,13 @@ PY
     shardmajor) run pytest_shardmajor 600 python -u -m pytest tests/test_gpu_shardmajor.py -m gpu -x -v --timeout 120 --timeout-method thread ;;
     masks)  run pytest_masks 600 python -u -m pytest tests/test_gpu_masks.py -m gpu -x -v --timeout 120 --timeout-method thread ;;
     mixed)  for wl in small_mixed encdec_mixed small; do
-              run bench_$wl 300 python bench.py --workload $wl --no-cpu
+              run bench_$wl 300 python bench.py --workload $wl --full --no-cpu
             done ;;
     prof_mixed) for wl in small_mixed encdec_mixed; do
               run prof_$wl 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$wl -o run --output-format csv -- python3 bench.py --no-cpu --steps 20 --workload $wl
             done ;;
     small1k) for wl in ${SMALL_WLS:-small1k small1k_p4 small1k_p1}; do
-              run bench_$wl 300 python bench.py --workload $wl --no-cpu
+              run bench_$wl 300 python bench.py --workload $wl --full --no-cpu
               run prof_$wl 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$wl -o run --output-format csv -- python3 bench.py --no-cpu --steps 10 --workload $wl
               run pmc_fetch_$wl 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_$wl -o run --output-format csv -- python3 bench.py --no-cpu --steps 5 --workload $wl
               run pmc_write_$wl 300 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_$wl -o run --output-format csv -- python3 bench.py --no-cpu --steps 5 --workload $wl
@@ -110,7 +110,7 @@ PY
     avail)  run avail 120 rocprofv3 --list-avail ;;
     dec4get) # BASELINE config 3 as Client.decode runs it: fused and unfused Get lines + kernel stats
             for wl in dec4_get dec4_upstream; do
-              run bench_$wl 600 python bench.py --workload $wl
+              run bench_$wl 600 python bench.py --workload $wl --full
               run prof_$wl 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$wl -o run --output-format csv -- python3 bench.py --no-cpu --no-pmc --steps 20 --workload $wl
             done ;;
     sq)     # issue / wait / clock counters per kernel (one pass per workload; 8 SQ + 2 GRBM slots)
@@ -129,12 +129,12 @@ PY
             done
             grep -h "^lib" gpurun_out/wsweep_w*.log > gpurun_out/wsweep_summary.txt || true ;;
     rehearse8) # the N = 8 scaling harness on the one-GPU box (8 gloo ranks sharing cuda:0), full batch
-            BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1 run rehearse8 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29538 bench.py --gpus 8 ;;
+            BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1 run rehearse8 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29538 bench.py --gpus 8 --full ;;
     pcie)   run pcie 300 ./tools/pcie_bench ;;
     example) run example 300 python examples/client_example.py --loopback --addr 127.0.0.1:16378 ;;
-    rehearse2) BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1 run rehearse2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --no-cpu --copies 2 ;;
+    rehearse2) BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1 run rehearse2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --full --no-cpu --copies 2 ;;
     trace_dev) run bench_trace_dev 900 python bench.py --workload trace --steps 3 --warmup 1 --devices ${TRACE_DEVICES:-1} ;;
-    torchrun1) run torchrun1 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --no-cpu ;;
+    torchrun1) run torchrun1 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --full --no-cpu ;;
     latency) run bench_latency 600 python bench.py --workload latency --steps 200 --warmup 10 ;;
     trace)  run bench_trace 900 python bench.py --workload trace --steps 3 --warmup 1 ;;
     kbench) for sh in ${KSHAPES:-enc10_2 dec10_2 enc10_4 rdata10_4 decx10_4 ver10_2 ver10_4}; do
