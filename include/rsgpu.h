@@ -304,6 +304,68 @@ int rsgpu_reconstruct_dev_masks(rsgpu_ctx *ctx, void *d_base, const uint32_t *d_
                                 size_t pitch, size_t obj_stride, int nobj, int data_only,
                                 uint32_t *d_status, void *stream);
 
+/* ---- corrupted-shard location and repair ---------------------------------
+ * A shard that arrives silently corrupted (present, right length, wrong
+ * bytes) makes Client.decode's Verify fail before and after Reconstruct
+ * (ecRedis.go:404-427) and the Get is lost.  The check rows the fused decode
+ * computes for the present shards beyond the first `data` are the syndromes
+ * of a punctured MDS code: with two or more of them the ONE bad shard can be
+ * named, and rebuilt as if it had not arrived.
+ * For one erasure pattern: Q = the present shards in index order, S = the
+ * first `data` of them (the survivors, as everywhere in this library), E =
+ * the remaining X = |Q| - data extras, C = G[E] x inv(G[S]) (X x data) and
+ * H = [C | I_X] over the columns S then E.  s(c) = H x y(c) are the X
+ * syndromes of byte column c < shard_len (pad bytes take no part, missing
+ * rows are never read).  An object is
+ *   clean        when every s(c) is zero;
+ *   located at shard order[q] when it is not clean and exactly one column
+ *                position q is alive: for every byte column c and row pair
+ *                a < b, H[b][q] (x) s_a(c) == H[a][q] (x) s_b(c) (s(c) is
+ *                parallel to column q);
+ *   unlocatable  otherwise (two or more shards corrupted; or a matrix that is
+ *                not MDS, e.g. PAR1, whose columns can be parallel).
+ * Errors, checked on the host in this order before any device is touched:
+ *   fewer than data+2 shards present            RSGPU_ERR_TOO_FEW_SHARDS
+ *   X > 4                                       RSGPU_ERR_NOT_IMPLEMENTED
+ *   data+parity > 16                            RSGPU_ERR_NOT_IMPLEMENTED
+ *   survivors' matrix singular                  RSGPU_ERR_SINGULAR
+ *   misaligned or oversized layout              RSGPU_ERR_INVALID_ARG */
+#define RSGPU_LOC_CLEAN (-1)       /* every syndrome is zero */
+#define RSGPU_LOC_UNLOCATABLE (-2) /* inconsistent, and no single shard explains it */
+
+/* Host only (no device): H (X x (data+X), row-major) and order (data+X shard
+ * indices, S then E) of the pattern `present` (data+parity flags), *x_out = X. */
+int rsgpu_check_matrix(rsgpu_ctx *ctx, const uint8_t *present, uint8_t *H_out, int *order_out, int *x_out);
+
+/* Locates in nobj device-resident objects sharing one pattern.  d_loc[o]
+ * (device int32) receives RSGPU_LOC_CLEAN, RSGPU_LOC_UNLOCATABLE or the shard
+ * index; d_masks[o] (device uint32, optional) the present mask with the
+ * located shard cleared (unchanged for clean and unlocatable objects), ready
+ * for rsgpu_decode_dev_masks.  Layout as the *_dev_masks calls (16-B aligned
+ * d_base, pitch and obj_stride, (data+parity)*pitch < 4 GiB, either
+ * orientation).  Asynchronous on `stream`; after a first call it issues only
+ * stream-ordered work and may be captured into a HIP graph. */
+int rsgpu_locate_dev(rsgpu_ctx *ctx, const void *d_base, const uint8_t *present, size_t shard_len, size_t pitch,
+                     size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, void *stream);
+
+/* rsgpu_locate_dev, then rsgpu_decode_dev_masks on d_masks (required: nobj
+ * words of caller scratch): missing rows and the located row are rebuilt in
+ * place and the remaining extras checked.  d_status[o] is that call's: 0
+ * healed or good, 1 still inconsistent (unlocatable objects: their present
+ * rows are left as they were). */
+int rsgpu_repair_dev(rsgpu_ctx *ctx, void *d_base, const uint8_t *present, size_t shard_len, size_t pitch,
+                     size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, uint32_t *d_status,
+                     void *stream);
+
+/* Per-object host calls (shards / lens as rsgpu_decode; always the stream
+ * path, the resident worker is not involved).  rsgpu_locate: *loc as d_loc
+ * above.  rsgpu_repair: fills the missing shards as rsgpu_decode does and,
+ * when a shard was located and the object then checks out, rewrites that
+ * shard in the caller's buffer (no other present shard is modified); *ok = 1
+ * when the object is good or healed. */
+int rsgpu_locate(rsgpu_ctx *ctx, const uint8_t *const *shards, const size_t *lens, int nshards, int *loc);
+int rsgpu_repair(rsgpu_ctx *ctx, uint8_t *const *shards, const size_t *lens, int nshards, int *loc, int *ok);
+
 /* ---- shard-major Get batches on whole lines ------------------------------
  * A Get batch of small objects decodes fastest shard-major through the
  * *_dev_masks calls with every piece on whole 128-B lines: at a 112-B stride

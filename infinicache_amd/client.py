@@ -52,6 +52,7 @@ class DataEntry:  # client.go:23-32
     Duration: float = 0.0
     AllGood: bool = False
     Corrupted: bool = False
+    Repaired: Optional[int] = None  # decode healed this silently corrupted shard (Client(repair=True))
 
 
 class ecRet:  # client.go:155-189
@@ -95,7 +96,7 @@ class Conn:
 
 class Client:
     def __init__(self, dataShards: int, parityShards: int, ecMaxGoroutine: int, *, device: int = -1,
-                 fused_decode: bool = True):
+                 fused_decode: bool = True, repair: bool = False):
         self.Conns: Dict[str, List[Optional[Conn]]] = {}
         self.EC = NewEncoder(dataShards, parityShards, ecMaxGoroutine, device=device)
         self.DataShards = dataShards
@@ -104,6 +105,9 @@ class Client:
         self.Data = DataEntry()
         self.members: List[str] = []
         self.fused_decode = fused_decode
+        # off: decode gives up on a silently corrupted shard exactly as the
+        # reference; on: it asks the codec to name and rebuild it (EC.Repair)
+        self.repair = repair
         self._pool = ThreadPoolExecutor(max_workers=max(self.Shards, 1))
 
     # ------------------------------------------------------------ dialing
@@ -175,6 +179,7 @@ class Client:
         except RSError:
             stats.AllGood = False  # nil shards: (false, ErrShardSize), no math
         if not stats.AllGood:
+            missing = [i for i, s in enumerate(data) if s is None or len(s) == 0]
             if self.fused_decode and hasattr(self.EC, "DecodeVerify"):
                 stats.Corrupted = self.EC.DecodeVerify(data)
             else:
@@ -183,6 +188,20 @@ class Client:
                     stats.Corrupted = self.EC.Verify(data)
                 except RSError:
                     stats.Corrupted = False
+            if not stats.Corrupted and self.repair and hasattr(self.EC, "Repair"):
+                # a shard arrived with wrong bytes: with two or more extra
+                # shards their check rows name it, and it is rebuilt in place.
+                # (The rows Reconstruct just filled came from the bad shard
+                # too: they are missing again as far as Repair is concerned.)
+                for i in missing:
+                    data[i] = None
+                try:
+                    loc, ok = self.EC.Repair(data)
+                except RSError:
+                    loc, ok = -2, False
+                if loc >= 0 and ok:
+                    stats.Repaired = loc
+                    stats.Corrupted = True
             if not stats.Corrupted:
                 raise RSError("Verification failed after reconstruction, data could be corrupted")
         out = io.BytesIO()
@@ -235,6 +254,7 @@ class Client:
         for f in futs:
             f.result()
         stats.RecLatency = time.time() - stats.Begin
+        stats.Repaired = None
         chunks: List[Optional[bytes]] = [None] * ret.Len()
         failed = []
         for i in range(ret.Len()):
@@ -248,6 +268,8 @@ class Client:
         except RSError:
             return stats.ReqId, None, False
         stats.Duration = time.time() - stats.Begin
+        if stats.Repaired is not None and stats.Repaired not in failed:
+            failed.append(stats.Repaired)  # recover re-Sets the healed chunk
         if failed:
             self.recover(host, key, str(uuid.uuid4()), chunks, failed)
         return stats.ReqId, reader, True

@@ -31,6 +31,7 @@
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "gf_apply.h"
+#include "gf_locate.h"
 #include "gf_masked.h"
 #include "gf_worker.h"
 
@@ -634,12 +635,13 @@ int run_masked(rsgpu_ctx *ctx, const AtlasView &A, AtlasMode mode, const Layout 
     // Inside a stream capture (a HIP graph): the scratch ring's event waits
     // and first-use allocations are not capturable, and a replay must not
     // share a ring slot with later calls; the counters then come from a
-    // stream-ordered allocation the graph owns (alloc + memset + free nodes)
+    // stream-ordered allocation the graph owns (alloc, a zeroing kernel, free)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
         uint32_t *tmp = nullptr;
         HIP_TRY(hipMallocAsync((void **)&tmp, (size_t)L.nobj * 2 * sizeof(uint32_t), st));
-        hipError_t e = hipMemsetAsync(tmp, 0, (size_t)L.nobj * 2 * sizeof(uint32_t), st);
+        // zeroed by a kernel, not a memset node (gf_locate.h launch_zero_u32)
+        hipError_t e = launch_zero_u32(tmp, (size_t)L.nobj * 2, st);
         if (e == hipSuccess) e = launch_masked(A, L, d_masks, d_status, tmp, tmp + L.nobj, st);
         const hipError_t f = hipFreeAsync(tmp, st);
         if (e != hipSuccess) return hip_fail(e, "launch_masked (capture)");
@@ -1385,6 +1387,223 @@ int rsgpu_reconstruct_dev_masks(rsgpu_ctx *ctx, void *d_base, const uint32_t *d_
     return dev_masks(ctx, d_base, d_masks, shard_len, pitch, obj_stride, nobj,
                      data_only ? kAtlasData : kAtlasReconstruct, d_status, stream);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------- locate / repair
+// A second use of the fused decode's check rows (gf_locate.h): with X >= 2
+// extras the syndromes name the one silently corrupted shard, and the masked
+// decode rebuilds it as if it had not arrived.
+
+namespace {
+
+// Host part of one pattern's locator, every check of the error table in
+// include/rsgpu.h in its order (no device needed).  C (optional) receives the
+// X x k matrix G[E] x inv(G[S]).
+int build_locate(rsgpu_ctx *ctx, const uint8_t *present, LocPlan &P, std::vector<uint8_t> *C) {
+    const int k = ctx->k, n = ctx->n;
+    int np = 0;
+    for (int i = 0; i < n; ++i) np += present[i] != 0;
+    if (np < k + kLocMinX) return RSGPU_ERR_TOO_FEW_SHARDS;
+    if (np - k > kLocMaxX) return RSGPU_ERR_NOT_IMPLEMENTED;
+    if (n > kLocMaxN) return RSGPU_ERR_NOT_IMPLEMENTED;
+    std::vector<int> surv, extra;
+    for (int i = 0; i < n; ++i)
+        if (present[i]) (surv.size() < (size_t)k ? surv : extra).push_back(i);
+    std::vector<uint8_t> inv;
+    int e = ctx->inverse(surv, inv);
+    if (e) return e;
+    P.K = k;
+    P.X = np - k;
+    P.nrows = n;
+    P.present = 0;
+    for (int q = 0; q < np; ++q) {
+        P.order[q] = (uint8_t)(q < k ? surv[q] : extra[q - k]);
+        P.present |= 1u << P.order[q];
+    }
+    const GF &g = gf();
+    if (C) C->assign((size_t)P.X * k, 0);
+    for (int r = 0; r < P.X; ++r)
+        for (int s = 0; s < k; ++s) {
+            uint8_t a = 0;
+            for (int c = 0; c < k; ++c) a ^= g.mul(ctx->row(extra[r])[c], inv[(size_t)c * k + s]);
+            coef_tables(a, &P.tab[((size_t)s * P.X + r) * kCoefWords]);
+            if (C) (*C)[(size_t)r * k + s] = a;
+        }
+    return RSGPU_OK;
+}
+
+// the *_dev_masks layout rules (16-B aligned rows, rows of one object < 4 GiB)
+int check_locate_layout(const rsgpu_ctx *ctx, const void *d_base, size_t shard_len, size_t pitch, size_t obj_stride,
+                        int nobj) {
+    int e = check_layout(ctx, d_base, shard_len, pitch, obj_stride, nobj);
+    if (e) return e == RSGPU_ERR_SHARD_NO_DATA ? e : RSGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_base & 15) || (pitch & 15) || (obj_stride & 15)) return RSGPU_ERR_INVALID_ARG;
+    return RSGPU_OK;
+}
+
+// launch_locate with its zeroed per-object scratch: the status ring, or inside
+// a stream capture the result words themselves
+int run_locate(rsgpu_ctx *ctx, const LocPlan &P, const Layout &L, int32_t *d_loc, uint32_t *d_masks, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+        // Inside a stream capture the ring's event waits are not capturable
+        // and a replay must not share a ring slot with later calls: the
+        // caller's own result words collect the masks, zeroed by a kernel of
+        // the same chain (the finish kernel reads each word before it writes it)
+        HIP_TRY(launch_locate(P, L, (uint32_t *)d_loc, d_loc, d_masks, st, true));
+        return RSGPU_OK;
+    }
+    StatusScratch::Slot *sc = nullptr;
+    HIP_TRY(ctx->scratch.acquire((size_t)L.nobj, st, sc));
+    const hipError_t e = launch_locate(P, L, sc->d, d_loc, d_masks, st);
+    const hipError_t e2 = ctx->scratch.release(sc, st, e == hipSuccess);
+    if (e != hipSuccess) return hip_fail(e, "launch_locate");
+    if (e2 != hipSuccess) return hip_fail(e2, "locate scratch");
+    return RSGPU_OK;
+}
+
+int locate_dev(rsgpu_ctx *ctx, const void *d_base, const uint8_t *present, size_t shard_len, size_t pitch,
+               size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, bool repair, uint32_t *d_status,
+               void *stream) {
+    if (!ctx || !present) return RSGPU_ERR_INVALID_ARG;
+    LocPlan P;
+    int e = build_locate(ctx, present, P, nullptr);
+    if (e) return e;
+    if ((e = check_locate_layout(ctx, d_base, shard_len, pitch, obj_stride, nobj))) return e;
+    if (nobj > 0 && (!d_loc || (repair && (!d_masks || !d_status)))) return RSGPU_ERR_INVALID_ARG;
+    DeviceGuard dg_;
+    if ((e = ctx->use_device(dg_))) return e;
+    if (nobj == 0) return RSGPU_OK;
+    Layout L{(uint8_t *)const_cast<void *>(d_base), obj_stride, pitch, shard_len, nobj};
+    if ((e = run_locate(ctx, P, L, d_loc, d_masks, (hipStream_t)stream))) return e;
+    if (!repair) return RSGPU_OK;
+    return dev_masks(ctx, L.base, d_masks, shard_len, pitch, obj_stride, nobj, kAtlasDecode, d_status, stream);
+}
+
+// One object from host shards through a staging slot (the stream path): the
+// present rows go up, locate (and, for repair, the masked decode) runs on the
+// image, the result words and the rebuilt rows come back.
+int locate_host(rsgpu_ctx *ctx, uint8_t *const *shards, const size_t *lens, int nshards, bool repair, int *loc,
+                int *ok) {
+    if (!ctx || !shards || !lens || !loc || (repair && !ok)) return RSGPU_ERR_INVALID_ARG;
+    *loc = kLocUnlocatable;
+    if (ok) *ok = 0;
+    if (nshards != ctx->n) return RSGPU_ERR_TOO_FEW_SHARDS;
+    size_t size;
+    int e = check_shards(lens, nshards, true, &size);
+    if (e) return e;
+    const int n = ctx->n;
+    std::vector<uint8_t> present((size_t)n);
+    for (int i = 0; i < n; ++i) present[i] = lens[i] != 0;
+    LocPlan P;
+    if ((e = build_locate(ctx, present.data(), P, nullptr))) return e;
+    const size_t pitch = round_up(size, 16), img = (size_t)n * pitch;
+    if (img >= ((size_t)1 << 32)) return RSGPU_ERR_INVALID_ARG;
+    if (repair)
+        for (int i = 0; i < n; ++i)
+            if (!present[i] && !shards[i]) return RSGPU_ERR_INVALID_ARG;
+    DeviceGuard dg_;
+    if ((e = ctx->use_device(dg_))) return e;
+    std::unique_ptr<Slot> s;
+    if ((e = ctx->get_slot(round_up(img + 16, 256), s))) return e;
+    // result words behind the image: loc, mask, status
+    int32_t *d_loc = (int32_t *)(s->d + img);
+    uint32_t *d_mask = (uint32_t *)(s->d + img) + 1, *d_status = (uint32_t *)(s->d + img) + 2;
+    const uint32_t *h_res = (const uint32_t *)(s->h + img);
+    hipError_t he = hipSuccess;
+    for (int i = 0; i < n && he == hipSuccess; ++i) {
+        if (!present[i]) continue;
+        std::memcpy(s->h + (size_t)i * pitch, shards[i], size);
+        he = hipMemcpyAsync(s->d + (size_t)i * pitch, s->h + (size_t)i * pitch, size, hipMemcpyHostToDevice, s->stream);
+    }
+    auto fail = [&](hipError_t err, int code) {
+        (void)hipStreamSynchronize(s->stream);  // nothing in flight may touch a pooled slot
+        ctx->put_slot(std::move(s));
+        return code ? code : hip_fail(err, "locate_host");
+    };
+    if (he != hipSuccess) return fail(he, 0);
+    Layout L{s->d, img, pitch, size, 1};
+    if ((e = run_locate(ctx, P, L, d_loc, d_mask, s->stream))) return fail(hipSuccess, e);
+    if (repair) {
+        AtlasView A;
+        e = ctx->atlas_view(kAtlasDecode, A);
+        if (e == RSGPU_OK) e = run_masked(ctx, A, kAtlasDecode, L, d_mask, d_status, s->stream);
+        else if (e == RSGPU_ERR_NOT_IMPLEMENTED) e = dev_masks_host(ctx, L, d_mask, kAtlasDecode, d_status, s->stream);
+        if (e) return fail(hipSuccess, e);
+    }
+    he = hipMemcpyAsync((void *)h_res, s->d + img, 12, hipMemcpyDeviceToHost, s->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
+    if (he != hipSuccess) return fail(he, 0);
+    const int32_t where = (int32_t)h_res[0];
+    const bool good = repair && h_res[2] == kStatusOk;
+    if (repair) {  // the rows the decode rebuilt: the missing ones and the located one
+        std::vector<int> back;
+        for (int i = 0; i < n; ++i)
+            if (!present[i] || (i == where && good)) back.push_back(i);
+        for (int i : back) {
+            he = hipMemcpyAsync(s->h + (size_t)i * pitch, s->d + (size_t)i * pitch, size, hipMemcpyDeviceToHost, s->stream);
+            if (he != hipSuccess) break;
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
+        if (he != hipSuccess) return fail(he, 0);
+        for (int i : back) std::memcpy(shards[i], s->h + (size_t)i * pitch, size);
+    }
+    *loc = where;
+    if (ok) *ok = good;
+    ctx->put_slot(std::move(s));
+    return RSGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsgpu_check_matrix(rsgpu_ctx *ctx, const uint8_t *present, uint8_t *H_out, int *order_out, int *x_out) {
+    if (!ctx || !present || !H_out || !order_out || !x_out) return RSGPU_ERR_INVALID_ARG;
+    LocPlan P;
+    std::vector<uint8_t> C;
+    int e = build_locate(ctx, present, P, &C);
+    if (e) return e;
+    const int w = P.K + P.X;
+    for (int r = 0; r < P.X; ++r)
+        for (int q = 0; q < w; ++q)
+            H_out[(size_t)r * w + q] = q < P.K ? C[(size_t)r * P.K + q] : (uint8_t)(q - P.K == r);
+    for (int q = 0; q < w; ++q) order_out[q] = P.order[q];
+    *x_out = P.X;
+    return RSGPU_OK;
+}
+
+int rsgpu_locate_dev(rsgpu_ctx *ctx, const void *d_base, const uint8_t *present, size_t shard_len, size_t pitch,
+                     size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, void *stream) {
+    RSGPU_FORWARD_DEV(rsgpu_locate_dev, d_base, d_base, present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks,
+                      stream)
+    return locate_dev(ctx, d_base, present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks, false, nullptr,
+                      stream);
+}
+
+int rsgpu_repair_dev(rsgpu_ctx *ctx, void *d_base, const uint8_t *present, size_t shard_len, size_t pitch,
+                     size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, uint32_t *d_status,
+                     void *stream) {
+    RSGPU_FORWARD_DEV(rsgpu_repair_dev, d_base, d_base, present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks,
+                      d_status, stream)
+    return locate_dev(ctx, d_base, present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks, true, d_status,
+                      stream);
+}
+
+int rsgpu_locate(rsgpu_ctx *ctx, const uint8_t *const *shards, const size_t *lens, int nshards, int *loc) {
+    RSGPU_FORWARD_RR(rsgpu_locate, shards, lens, nshards, loc);
+    return locate_host(ctx, const_cast<uint8_t *const *>(shards), lens, nshards, false, loc, nullptr);
+}
+
+int rsgpu_repair(rsgpu_ctx *ctx, uint8_t *const *shards, const size_t *lens, int nshards, int *loc, int *ok) {
+    RSGPU_FORWARD_RR(rsgpu_repair, shards, lens, nshards, loc, ok);
+    return locate_host(ctx, shards, lens, nshards, true, loc, ok);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ---------------------------------------------- variable-size device batches
 

@@ -124,6 +124,10 @@ def _check(code: int):
 
 MATRIX_KINDS = {"vandermonde": 0, "cauchy": 1, "par1": 2}
 
+# results of Locate / locate_dev (rsgpu.h RSGPU_LOC_*); >= 0 is a shard index
+LOC_CLEAN = -1
+LOC_UNLOCATABLE = -2
+
 # ---------------------------------------------------------------- helpers
 
 
@@ -368,6 +372,43 @@ class RSEncoder:
         one device pass; returns what the Verify after Reconstruct returns."""
         return self._reconstruct(shards, data_only=False, fused_verify=True)
 
+    # -- corrupted-shard location and repair (rsgpu.h; no upstream twin) ----
+    def check_matrix(self, present):
+        """rsgpu_check_matrix (host only): (H, order) of the pattern
+        ``present`` (k+p flags): H is X x (k+X) over the columns order =
+        survivors then extras."""
+        pr = (ctypes.c_uint8 * self.Shards)(*[1 if x else 0 for x in present])
+        H = np.zeros(self.ParityShards * self.Shards, dtype=np.uint8)
+        order = (ctypes.c_int * self.Shards)()
+        x = ctypes.c_int(0)
+        _check(self._L.rsgpu_check_matrix(self._ctx, pr, H.ctypes.data_as(_lib.u8p), order, ctypes.byref(x)))
+        w = self.DataShards + x.value
+        return H[:x.value * w].reshape(x.value, w).copy(), list(order[:w])
+
+    def Locate(self, shards: Sequence) -> int:
+        """The index of the one silently corrupted shard among the present
+        ones, LOC_CLEAN or LOC_UNLOCATABLE (needs k+2 present shards)."""
+        t = _ShardTable(shards)
+        loc = ctypes.c_int(LOC_UNLOCATABLE)
+        _check(self._L.rsgpu_locate(self._ctx, t.ptrs, t.lens, len(shards), ctypes.byref(loc)))
+        return loc.value
+
+    def Repair(self, shards: list):
+        """Locate, then rebuild: None entries are filled as in Reconstruct and
+        shards[loc] is healed in place.  Returns (loc, ok); ok is False when
+        the object is still inconsistent (nothing but missing shards written)."""
+        if not isinstance(shards, list):
+            raise InvalidArgument("shards must be a list (filled in place)")
+        bufs, missing = self._prepare_missing(shards, False)
+        t = _ShardTable(bufs, writable_idx=range(len(bufs)))  # any present shard may be the healed one
+        for i in missing:
+            t.lens[i] = 0
+        loc, ok = ctypes.c_int(LOC_UNLOCATABLE), ctypes.c_int(0)
+        _check(self._L.rsgpu_repair(self._ctx, t.ptrs, t.lens, len(shards), ctypes.byref(loc), ctypes.byref(ok)))
+        for i in missing:
+            shards[i] = bufs[i]
+        return loc.value, bool(ok.value)
+
     def Update(self, shards: Sequence, newDatashards: Sequence) -> None:
         t = _ShardTable(shards, writable_idx=range(len(shards)))
         nt = _ShardTable(newDatashards)
@@ -466,6 +507,23 @@ class RSEncoder:
         0 ok, 1 Verify-after-Reconstruct mismatch, 2 too few shards, 3 singular."""
         _check(self._L.rsgpu_decode_dev_masks(self._ctx, _dptr(base), _dptr(masks), shard_len, pitch,
                                               obj_stride, nobj, _dptr(status), _stream_handle(stream)))
+
+    def locate_dev(self, base, present, shard_len, pitch, obj_stride, nobj, loc, masks=None, stream=None):
+        """rsgpu_locate_dev: one pattern ``present`` for the batch; loc (nobj
+        int32 in HBM) receives LOC_CLEAN, LOC_UNLOCATABLE or the corrupted
+        shard's index, masks (optional, nobj uint32) the present mask with
+        that shard cleared, ready for decode_dev_masks."""
+        pr = (ctypes.c_uint8 * self.Shards)(*[1 if x else 0 for x in present])
+        _check(self._L.rsgpu_locate_dev(self._ctx, _dptr(base), pr, shard_len, pitch, obj_stride, nobj,
+                                        _dptr(loc), _dptr(masks), _stream_handle(stream)))
+
+    def repair_dev(self, base, present, shard_len, pitch, obj_stride, nobj, loc, masks, status, stream=None):
+        """rsgpu_repair_dev: locate_dev, then decode_dev_masks on ``masks``
+        (nobj uint32 of scratch): missing rows and the located row rebuilt in
+        place; status 0 healed or good, 1 still inconsistent."""
+        pr = (ctypes.c_uint8 * self.Shards)(*[1 if x else 0 for x in present])
+        _check(self._L.rsgpu_repair_dev(self._ctx, _dptr(base), pr, shard_len, pitch, obj_stride, nobj,
+                                        _dptr(loc), _dptr(masks), _dptr(status), _stream_handle(stream)))
 
     def reconstruct_dev_masks(self, base, masks, shard_len, pitch, obj_stride, nobj, data_only=False,
                               status=None, stream=None):
