@@ -357,6 +357,64 @@ int rsgpu_repair_dev(rsgpu_ctx *ctx, void *d_base, const uint8_t *present, size_
                      size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, uint32_t *d_status,
                      void *stream);
 
+/* ---- per-object patterns from device masks
+ * A Get batch is mixed-pattern (rsgpu_shardmajor_layout below): every object
+ * has its own present set.  These calls take the patterns as present bitmasks
+ * in HBM, as rsgpu_decode_dev_masks does, and resolve each one on the device
+ * against a per-context table of every pattern the locator serves (built and
+ * uploaded by the first call; at most about 15 MB for a code of <= 16 shards).
+ * No host synchronisation, no per-pattern launches.
+ *
+ * Per object o the semantics are exactly rsgpu_locate_dev's, applied to the
+ * pattern d_present[o] & ((1 << (data+parity)) - 1): survivors = the first
+ * `data` present shards in index order, extras = the rest; H, the syndromes
+ * and the clean / located / unlocatable cases as defined above.  Missing rows
+ * are never read, pad bytes take no part.  What is a call-level error there is
+ * a per-object result here: an object whose pattern the locator does not
+ * serve gets one of the codes below in d_loc[o], and none of its rows is read. */
+#define RSGPU_LOC_TOO_FEW  (-3)  /* fewer than data+2 shards present: nothing can be named */
+#define RSGPU_LOC_TOO_MANY (-4)  /* more than 4 extras (as rsgpu_locate_dev's X > 4) */
+#define RSGPU_LOC_SINGULAR (-5)  /* survivors' matrix singular (non-MDS matrices) */
+
+/* Host only, no device.  What the locator makes of the pattern present_mask
+ * (bit i: shard i present; bits >= data+parity ignored): the number of
+ * extras X (2..4) when it serves the pattern, else RSGPU_LOC_TOO_FEW,
+ * _TOO_MANY or _SINGULAR, tested in that order.  data+parity > 16:
+ * RSGPU_ERR_NOT_IMPLEMENTED. */
+int rsgpu_locate_pattern(rsgpu_ctx *ctx, uint32_t present_mask);
+
+/* d_loc[o] (device int32): the shard index, RSGPU_LOC_CLEAN,
+ * RSGPU_LOC_UNLOCATABLE, or RSGPU_LOC_TOO_FEW / _TOO_MANY / _SINGULAR.
+ * d_masks[o] (device uint32, optional; may be d_present itself): the object's
+ * present mask truncated to data+parity bits, with the located shard cleared;
+ * for every other object that truncated mask, otherwise unchanged.
+ * Layout as the *_dev_masks calls.  Errors, checked on the host in this order
+ * before any device is touched:
+ *   NULL ctx, or NULL d_present with nobj > 0   RSGPU_ERR_INVALID_ARG
+ *   data+parity > 16                            RSGPU_ERR_NOT_IMPLEMENTED
+ *   shard_len == 0                              RSGPU_ERR_SHARD_NO_DATA
+ *   misaligned or oversized layout              RSGPU_ERR_INVALID_ARG
+ *   NULL d_loc (repair: d_masks, d_status)      RSGPU_ERR_INVALID_ARG
+ *   no usable device                            RSGPU_ERR_NO_DEVICE
+ * nobj == 0 succeeds.  Asynchronous on `stream`; after a first call has built
+ * and uploaded the table the call issues only stream-ordered work (no
+ * allocation) and may be captured into a HIP graph.  Rows of at most 2048
+ * bytes in a batch of more than one object are located several whole objects
+ * per workgroup; RSGPU_LOCATE_LANES=0 in the environment at load keeps the
+ * one-object-per-workgroup form for them (same results). */
+int rsgpu_locate_dev_masks(rsgpu_ctx *ctx, const void *d_base, const uint32_t *d_present, size_t shard_len,
+                           size_t pitch, size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks,
+                           void *stream);
+
+/* rsgpu_locate_dev_masks, then rsgpu_decode_dev_masks on d_masks (required),
+ * on the same stream.  d_status[o] is that decode's own: 0 healed or good (an
+ * object the locator does not serve is simply decoded), 1 still inconsistent
+ * (unlocatable objects keep their present rows as they were), 2 too few
+ * shards, 3 singular. */
+int rsgpu_repair_dev_masks(rsgpu_ctx *ctx, void *d_base, const uint32_t *d_present, size_t shard_len, size_t pitch,
+                           size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, uint32_t *d_status,
+                           void *stream);
+
 /* Per-object host calls (shards / lens as rsgpu_decode; always the stream
  * path, the resident worker is not involved).  rsgpu_locate: *loc as d_loc
  * above.  rsgpu_repair: fills the missing shards as rsgpu_decode does and,

@@ -1,7 +1,7 @@
 """infinicache_amd — MI355X-native Reed-Solomon erasure coding for the
 InfiniCache client (drop-in for reedsolomon.Encoder under
 /root/reference/client/ec.go).  See DESIGN.md."""
-from .ec import (ALL_DEVICES, LOC_CLEAN, LOC_UNLOCATABLE, DummyEncoder, ErrInvalidInput, ErrInvShardNum, ErrMaxShardNum,  # noqa: F401
+from .ec import (ALL_DEVICES, LOC_CLEAN, LOC_SINGULAR, LOC_TOO_FEW, LOC_TOO_MANY, LOC_UNLOCATABLE, DummyEncoder, ErrInvalidInput, ErrInvShardNum, ErrMaxShardNum,  # noqa: F401
                  ErrNotImplemented, ErrReconstructRequired, ErrShardNoData, ErrShardSize,
                  ErrShortData, ErrSingular, ErrTooFewShards, HipError, InvalidArgument, New,
                  NewEncoder, NoDevice, RSEncoder, RSError, device_count, device_ok, host_alloc,
@@ -13,5 +13,5 @@ __all__ = [
     "ErrSingular", "ErrShortData", "ErrReconstructRequired", "ErrInvalidInput",
     "ErrNotImplemented", "InvalidArgument", "NoDevice", "HipError", "host_alloc",
     "host_register", "host_unregister", "shardmajor_layout", "ALL_DEVICES", "retired_stats",
-    "set_slab_bytes", "LOC_CLEAN", "LOC_UNLOCATABLE",
+    "set_slab_bytes", "LOC_CLEAN", "LOC_UNLOCATABLE", "LOC_TOO_FEW", "LOC_TOO_MANY", "LOC_SINGULAR",
 ]

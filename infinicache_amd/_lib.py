@@ -29,6 +29,7 @@ EXPORTS = (
     "rsgpu_worker_start", "rsgpu_worker_stop", "rsgpu_worker_stats", "rsgpu_shardmajor_layout",
     "rsgpu_copy_pieces", "rsgpu_retired_stats", "rsgpu_set_slab_bytes",
     "rsgpu_check_matrix", "rsgpu_locate_dev", "rsgpu_repair_dev", "rsgpu_locate", "rsgpu_repair",
+    "rsgpu_locate_pattern", "rsgpu_locate_dev_masks", "rsgpu_repair_dev_masks",
 )
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -101,6 +102,9 @@ def load():
     L.rsgpu_check_matrix.argtypes = [vp, u8p, u8p, intp, intp]
     L.rsgpu_locate_dev.argtypes = [vp, vp, u8p, sz, sz, sz, ci, vp, vp, vp]
     L.rsgpu_repair_dev.argtypes = [vp, vp, u8p, sz, sz, sz, ci, vp, vp, vp, vp]
+    L.rsgpu_locate_pattern.argtypes = [vp, ctypes.c_uint32]
+    L.rsgpu_locate_dev_masks.argtypes = [vp, vp, vp, sz, sz, sz, ci, vp, vp, vp]
+    L.rsgpu_repair_dev_masks.argtypes = [vp, vp, vp, sz, sz, sz, ci, vp, vp, vp, vp]
     L.rsgpu_locate.argtypes = [vp, u8pp, szp, ci, intp]
     L.rsgpu_repair.argtypes = [vp, u8pp, szp, ci, intp, intp]
     L.rsgpu_encode_image.argtypes = [vp, vp, sz, ci]

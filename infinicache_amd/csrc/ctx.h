@@ -19,6 +19,7 @@
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "gf_apply.h"
+#include "gf_locate.h"
 
 namespace rsgpu {
 
@@ -161,6 +162,32 @@ struct Atlas {
     }
     ~Atlas() { free_dev(); }
 };
+// The locator's atlas (gf_locate.h): every pattern rsgpu_locate_dev_masks
+// serves.  Host part and upload follow Atlas: one host build per code, shared
+// by a multi-device context's sub-contexts, one device copy per context.  The
+// pattern table stays on the host (rsgpu_locate_pattern answers from it).
+struct LocAtlas {
+    std::once_flag host_once;
+    int host_err = 0;
+    std::mutex dev_mu;
+    bool dev_done = false;
+    int32_t *d_pat = nullptr;
+    LocRec *d_recs = nullptr;
+    uint32_t *d_tabs = nullptr;
+    std::vector<int32_t> h_pat;
+    std::vector<LocRec> h_recs;
+    std::vector<uint32_t> h_tabs;
+    LocAtlasView view;
+    void free_dev() {
+        retire(d_pat, false);
+        retire(d_recs, false);
+        retire(d_tabs, false);
+        d_pat = nullptr;
+        d_recs = nullptr;
+        d_tabs = nullptr;
+    }
+    ~LocAtlas() { free_dev(); }
+};
 // Estimated bytes of an atlas's kernel tables (before building it): the
 // host-flag *_dev_multi calls take the atlas path only below a modest size
 // and keep the host-planned path for codes whose atlas would be large.
@@ -179,6 +206,7 @@ struct rsgpu_ctx {
     rsgpu::Pipeline pipe;  // batch host API (pipeline.cpp)
     rsgpu::MultiWorkspace multi_ws;  // mixed-pattern device launches
     rsgpu::Atlas atlas[3];           // device-resolved patterns, per AtlasMode
+    rsgpu::LocAtlas loc_atlas;       // the locator's patterns (rsgpu_locate_dev_masks)
     uint32_t *d_ctab = nullptr;      // [256][8] coefficient tables (gf_apply_lanes)
     std::mutex ctab_mu;              // guards the d_ctab upload (retried after a failure)
     rsgpu::StatusScratch scratch;    // multi-reporter status of the masked decode
@@ -413,6 +441,10 @@ struct rsgpu_ctx {
     // the uploaded atlas the kernels read
     int atlas_host(AtlasMode mode, const Atlas *&out);
     int atlas_view(AtlasMode mode, AtlasView &out);
+    int ctab_dev();  // uploads d_ctab on first use
+    // the locator's atlas: host part (no device needed), uploaded view
+    int loc_atlas_host(const LocAtlas *&out);
+    int loc_atlas_view(LocAtlasView &out);
 
     // ---- staging slots
     int get_slot(size_t bytes, std::unique_ptr<Slot> &s) {

@@ -588,25 +588,28 @@ int rsgpu_ctx::atlas_host(AtlasMode mode, const Atlas *&out) {
     return A.host_err;
 }
 
+int rsgpu_ctx::ctab_dev() {
+    std::lock_guard<std::mutex> g(ctab_mu);
+    if (!d_ctab) {
+        std::vector<uint32_t> t(256 * kCtabStride, 0);
+        for (int c = 0; c < 256; ++c) coef_tables((uint8_t)c, &t[(size_t)c * kCtabStride]);
+        uint32_t *d = nullptr;
+        hipError_t he = hipMalloc(&d, t.size() * 4);
+        if (he == hipSuccess) he = upload(d, t.data(), t.size() * 4);
+        if (he != hipSuccess) {
+            retire(d, false);
+            return hip_fail(he, "atlas coefficient table");  // retried by the next call
+        }
+        d_ctab = d;
+    }
+    return RSGPU_OK;
+}
+
 int rsgpu_ctx::atlas_view(AtlasMode mode, AtlasView &out) {
     const Atlas *ah;
     int e = atlas_host(mode, ah);
     if (e) return e;
-    {
-        std::lock_guard<std::mutex> g(ctab_mu);
-        if (!d_ctab) {
-            std::vector<uint32_t> t(256 * kCtabStride, 0);
-            for (int c = 0; c < 256; ++c) coef_tables((uint8_t)c, &t[(size_t)c * kCtabStride]);
-            uint32_t *d = nullptr;
-            hipError_t he = hipMalloc(&d, t.size() * 4);
-            if (he == hipSuccess) he = upload(d, t.data(), t.size() * 4);
-            if (he != hipSuccess) {
-                retire(d, false);
-                return hip_fail(he, "atlas coefficient table");  // retried by the next call
-            }
-            d_ctab = d;
-        }
-    }
+    if ((e = ctab_dev())) return e;
     Atlas &D = atlas[mode];
     std::lock_guard<std::mutex> g(D.dev_mu);
     if (!D.dev_done) {
@@ -1555,9 +1558,181 @@ int locate_host(rsgpu_ctx *ctx, uint8_t *const *shards, const size_t *lens, int 
     return RSGPU_OK;
 }
 
+// The locator's atlas (gf_locate.h), host part: every mask of the code
+// classified in build_locate's own order (too few, too many, singular), one
+// record and table block per served pattern, each from build_locate itself so
+// the uniform and the masked calls cannot disagree.  At most about 15 MB
+// (RS(6+10): 32,318 patterns x 480 B of tables).
+int build_loc_atlas_host(rsgpu_ctx *ctx, LocAtlas &A) {
+    const int n = ctx->n, k = ctx->k;
+    const size_t nm = (size_t)1 << n;
+    const int xmax = std::max(kLocMinX, std::min(kLocMaxX, ctx->p));
+    const size_t tw = (size_t)k * xmax * kCoefWords;
+    A.h_pat.assign(nm, kLocTooFew);
+    std::vector<uint8_t> present((size_t)n), C;
+    for (size_t mask = 0; mask < nm; ++mask) {
+        const int np = __builtin_popcountll(mask);
+        if (np < k + kLocMinX) continue;
+        if (np - k > kLocMaxX) {
+            A.h_pat[mask] = kLocTooMany;
+            continue;
+        }
+        for (int i = 0; i < n; ++i) present[i] = (mask >> i) & 1;
+        LocPlan P;
+        const int e = build_locate(ctx, present.data(), P, &C);
+        if (e == RSGPU_ERR_SINGULAR) {
+            A.h_pat[mask] = kLocSingular;
+            continue;
+        }
+        if (e) return e;
+        const size_t slot = A.h_recs.size();
+        A.h_pat[mask] = (int32_t)slot;
+        LocRec rc;
+        std::memset(&rc, 0, sizeof rc);
+        rc.X = (uint32_t)P.X;
+        for (int q = 0; q < P.K + P.X; ++q) rc.order[q >> 3] |= (uint32_t)(P.order[q] & 15u) << (4 * (q & 7));
+        for (int r = 0; r < P.X; ++r)
+            for (int c = 0; c < k; ++c) rc.coef[r][c] = C[(size_t)r * k + c];
+        A.h_recs.push_back(rc);
+        A.h_tabs.resize((slot + 1) * tw, 0u);  // rows >= X stay zero
+        for (int c = 0; c < k; ++c)
+            for (int r = 0; r < P.X; ++r)
+                std::memcpy(&A.h_tabs[slot * tw + ((size_t)c * xmax + r) * kCoefWords],
+                            &P.tab[((size_t)c * P.X + r) * kCoefWords], kCoefWords * 4);
+    }
+    if (A.h_recs.empty()) {  // no pattern served (parity < 2): the kernels still take valid pointers
+        LocRec rc;
+        std::memset(&rc, 0, sizeof rc);
+        A.h_recs.push_back(rc);
+        A.h_tabs.assign(tw, 0u);
+    }
+    A.view.n = n;
+    A.view.k = k;
+    A.view.xmax = xmax;
+    return RSGPU_OK;
+}
+
+}  // namespace
+
+int rsgpu_ctx::loc_atlas_host(const LocAtlas *&out) {
+    if (n > kLocMaxN) return RSGPU_ERR_NOT_IMPLEMENTED;
+    rsgpu_ctx *owner = parent ? parent : this;  // one host build per code
+    LocAtlas &A = owner->loc_atlas;
+    std::call_once(A.host_once, [&] { A.host_err = build_loc_atlas_host(owner, A); });
+    out = &A;
+    return A.host_err;
+}
+
+int rsgpu_ctx::loc_atlas_view(LocAtlasView &out) {
+    const LocAtlas *ah;
+    int e = loc_atlas_host(ah);
+    if (e) return e;
+    if ((e = ctab_dev())) return e;
+    LocAtlas &D = loc_atlas;
+    std::lock_guard<std::mutex> g(D.dev_mu);
+    if (!D.dev_done) {
+        hipError_t he = hipMalloc(&D.d_pat, ah->h_pat.size() * 4);
+        if (he == hipSuccess) he = upload(D.d_pat, ah->h_pat.data(), ah->h_pat.size() * 4);
+        if (he == hipSuccess) he = hipMalloc(&D.d_recs, ah->h_recs.size() * sizeof(LocRec));
+        if (he == hipSuccess) he = upload(D.d_recs, ah->h_recs.data(), ah->h_recs.size() * sizeof(LocRec));
+        if (he == hipSuccess) he = hipMalloc(&D.d_tabs, ah->h_tabs.size() * 4);
+        if (he == hipSuccess) he = upload(D.d_tabs, ah->h_tabs.data(), ah->h_tabs.size() * 4);
+        if (he != hipSuccess) {
+            D.free_dev();
+            return hip_fail(he, "locator atlas upload");  // retried by the next call
+        }
+        D.view = ah->view;
+        D.view.pat = D.d_pat;
+        D.view.recs = D.d_recs;
+        D.view.tabs = D.d_tabs;
+        D.view.ctab = d_ctab;
+        D.dev_done = true;
+        // a context of its own drops the host images once they are on the
+        // device (the pattern table stays: rsgpu_locate_pattern)
+        if (ah == &D && subs.empty() && !parent) {
+            std::vector<LocRec>().swap(D.h_recs);
+            std::vector<uint32_t>().swap(D.h_tabs);
+        }
+    }
+    out = D.view;
+    return RSGPU_OK;
+}
+
+namespace {
+
+// launch_locate_masks with its scratch, as run_locate: the status ring when
+// eager, the caller's result words (zeroed by a kernel of the chain) inside a
+// stream capture.  The short-row form needs neither.
+int run_locate_masks(rsgpu_ctx *ctx, const LocAtlasView &A, const Layout &L, const uint32_t *d_present,
+                     int32_t *d_loc, uint32_t *d_masks, hipStream_t st) {
+    if (locate_lanes_form(L)) {
+        HIP_TRY(launch_locate_masks(A, L, d_present, nullptr, d_loc, d_masks, st));
+        return RSGPU_OK;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+        HIP_TRY(launch_locate_masks(A, L, d_present, (uint32_t *)d_loc, d_loc, d_masks, st, true));
+        return RSGPU_OK;
+    }
+    StatusScratch::Slot *sc = nullptr;
+    HIP_TRY(ctx->scratch.acquire((size_t)L.nobj, st, sc));
+    const hipError_t e = launch_locate_masks(A, L, d_present, sc->d, d_loc, d_masks, st);
+    const hipError_t e2 = ctx->scratch.release(sc, st, e == hipSuccess);
+    if (e != hipSuccess) return hip_fail(e, "launch_locate_masks");
+    if (e2 != hipSuccess) return hip_fail(e2, "locate scratch");
+    return RSGPU_OK;
+}
+
+int locate_dev_masks(rsgpu_ctx *ctx, const void *d_base, const uint32_t *d_present, size_t shard_len, size_t pitch,
+                     size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, bool repair, uint32_t *d_status,
+                     void *stream) {
+    if (!ctx || (nobj > 0 && !d_present)) return RSGPU_ERR_INVALID_ARG;
+    if (ctx->n > kLocMaxN) return RSGPU_ERR_NOT_IMPLEMENTED;
+    int e = check_locate_layout(ctx, d_base, shard_len, pitch, obj_stride, nobj);
+    if (e) return e;
+    if (nobj > 0 && (!d_loc || (repair && (!d_masks || !d_status)))) return RSGPU_ERR_INVALID_ARG;
+    DeviceGuard dg_;
+    if ((e = ctx->use_device(dg_))) return e;
+    if (nobj == 0) return RSGPU_OK;
+    LocAtlasView A;
+    if ((e = ctx->loc_atlas_view(A))) return e;
+    Layout L{(uint8_t *)const_cast<void *>(d_base), obj_stride, pitch, shard_len, nobj};
+    if ((e = run_locate_masks(ctx, A, L, d_present, d_loc, d_masks, (hipStream_t)stream))) return e;
+    if (!repair) return RSGPU_OK;
+    return dev_masks(ctx, L.base, d_masks, shard_len, pitch, obj_stride, nobj, kAtlasDecode, d_status, stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rsgpu_locate_pattern(rsgpu_ctx *ctx, uint32_t present_mask) {
+    if (!ctx) return RSGPU_ERR_INVALID_ARG;
+    const LocAtlas *A;
+    const int e = ctx->loc_atlas_host(A);
+    if (e) return e;
+    const uint32_t m = present_mask & ((1u << ctx->n) - 1u);
+    const int32_t slot = A->h_pat[m];
+    return slot < 0 ? slot : __builtin_popcount(m) - ctx->k;  // served: X
+}
+
+int rsgpu_locate_dev_masks(rsgpu_ctx *ctx, const void *d_base, const uint32_t *d_present, size_t shard_len,
+                           size_t pitch, size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks,
+                           void *stream) {
+    RSGPU_FORWARD_DEV(rsgpu_locate_dev_masks, d_base, d_base, d_present, shard_len, pitch, obj_stride, nobj, d_loc,
+                      d_masks, stream)
+    return locate_dev_masks(ctx, d_base, d_present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks, false,
+                            nullptr, stream);
+}
+
+int rsgpu_repair_dev_masks(rsgpu_ctx *ctx, void *d_base, const uint32_t *d_present, size_t shard_len, size_t pitch,
+                           size_t obj_stride, int nobj, int32_t *d_loc, uint32_t *d_masks, uint32_t *d_status,
+                           void *stream) {
+    RSGPU_FORWARD_DEV(rsgpu_repair_dev_masks, d_base, d_base, d_present, shard_len, pitch, obj_stride, nobj, d_loc,
+                      d_masks, d_status, stream)
+    return locate_dev_masks(ctx, d_base, d_present, shard_len, pitch, obj_stride, nobj, d_loc, d_masks, true,
+                            d_status, stream);
+}
 
 int rsgpu_check_matrix(rsgpu_ctx *ctx, const uint8_t *present, uint8_t *H_out, int *order_out, int *x_out) {
     if (!ctx || !present || !H_out || !order_out || !x_out) return RSGPU_ERR_INVALID_ARG;

@@ -127,6 +127,10 @@ MATRIX_KINDS = {"vandermonde": 0, "cauchy": 1, "par1": 2}
 # results of Locate / locate_dev (rsgpu.h RSGPU_LOC_*); >= 0 is a shard index
 LOC_CLEAN = -1
 LOC_UNLOCATABLE = -2
+# per object from locate_dev_masks / locate_pattern: patterns the locator does not serve
+LOC_TOO_FEW = -3
+LOC_TOO_MANY = -4
+LOC_SINGULAR = -5
 
 # ---------------------------------------------------------------- helpers
 
@@ -524,6 +528,33 @@ class RSEncoder:
         pr = (ctypes.c_uint8 * self.Shards)(*[1 if x else 0 for x in present])
         _check(self._L.rsgpu_repair_dev(self._ctx, _dptr(base), pr, shard_len, pitch, obj_stride, nobj,
                                         _dptr(loc), _dptr(masks), _dptr(status), _stream_handle(stream)))
+
+    def locate_pattern(self, mask):
+        """rsgpu_locate_pattern (host only): the number of extras X (2..4)
+        when the locator serves the present bitmask ``mask``, else
+        LOC_TOO_FEW, LOC_TOO_MANY or LOC_SINGULAR."""
+        r = self._L.rsgpu_locate_pattern(self._ctx, int(mask) & 0xFFFFFFFF)
+        if r < LOC_SINGULAR:
+            _check(r)
+        return r
+
+    def locate_dev_masks(self, base, present, shard_len, pitch, obj_stride, nobj, loc, masks=None, stream=None):
+        """rsgpu_locate_dev_masks: per-object patterns as device-resident
+        present bitmasks (present: nobj uint32 in HBM).  loc (nobj int32)
+        receives the corrupted shard's index, LOC_CLEAN, LOC_UNLOCATABLE, or
+        LOC_TOO_FEW / LOC_TOO_MANY / LOC_SINGULAR for an object whose pattern
+        the locator does not serve; masks (optional, may be ``present``) the
+        mask with the located shard cleared, ready for decode_dev_masks."""
+        _check(self._L.rsgpu_locate_dev_masks(self._ctx, _dptr(base), _dptr(present), shard_len, pitch, obj_stride,
+                                              nobj, _dptr(loc), _dptr(masks), _stream_handle(stream)))
+
+    def repair_dev_masks(self, base, present, shard_len, pitch, obj_stride, nobj, loc, masks, status, stream=None):
+        """rsgpu_repair_dev_masks: locate_dev_masks, then decode_dev_masks on
+        ``masks``; status is that decode's (0 healed or good, 1 still
+        inconsistent, 2 too few shards, 3 singular)."""
+        _check(self._L.rsgpu_repair_dev_masks(self._ctx, _dptr(base), _dptr(present), shard_len, pitch, obj_stride,
+                                              nobj, _dptr(loc), _dptr(masks), _dptr(status),
+                                              _stream_handle(stream)))
 
     def reconstruct_dev_masks(self, base, masks, shard_len, pitch, obj_stride, nobj, data_only=False,
                               status=None, stream=None):
